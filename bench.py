@@ -6,11 +6,18 @@ for collaborative ALBERT training (reference: examples/albert, ~20.9
 samples/s/peer on 1080 Ti-class GPUs, target_batch_size 4096) -- on N MI355X
 GPUs of one node, one process per GPU over RCCL/xGMI.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 For N>1 the driver launches this via torch.distributed.run with one rank per
 GPU; ranks read RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the environment.
 
-Synthetic data (random token ids of the benchmark shape), random-init weights.
+A plain run sets up, warms up, times exactly K steps and prints one JSON result
+line. --dump-outputs DIR additionally writes what the last timed step computed
+(loss, logits, updated parameters) as DIR/<name>.npy so two builds can be
+compared output for output. Everything beyond the headline figure belongs
+behind --full.
+
+Synthetic data (random token ids of the benchmark shape), random-init weights;
+both are seeded, so the same arguments give the same inputs on every run.
 """
 
 import argparse
@@ -27,6 +34,41 @@ BASELINE_SAMPLES_PER_SEC_PER_PEER = 20.9  # ALBERT collaborative tr
 
 def log(msg):
     print(f"[bench rank{os.environ.get('RANK', '0')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_MAX_ELEMENTS = 4 * 1024 * 1024  # per dumped array: 16 MB as float32, 3 arrays < 64 MB
+
+
+def _fixed_sample(flat, count, seed):
+    """`count` elements of a 1-d tensor at fixed positions (seeded, sorted), or
+    the whole tensor if it is no larger than that."""
+    if flat.numel() <= count:
+        return flat
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    index = torch.randint(0, flat.numel(), (count,), generator=gen).sort().values
+    return flat[index.to(flat.device)]
+
+
+def dump_outputs(dirname, loss, logits, parameters):
+    """Write what the last timed step returned (loss, logits) and left behind
+    (the updated model parameters) as float32 .npy files. Large arrays are
+    reduced to a fixed seeded sample so the whole dump stays below 64 MB."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    parameters = list(parameters)
+    per_param = max(1, DUMP_MAX_ELEMENTS // max(1, len(parameters)))
+    arrays = {
+        "loss": loss.detach().reshape(1),
+        "logits": _fixed_sample(logits.detach().reshape(-1), DUMP_MAX_ELEMENTS, seed=0),
+        "params": torch.cat([
+            _fixed_sample(p.detach().reshape(-1), per_param, seed=1 + i).float()
+            for i, p in enumerate(parameters)
+        ]),
+    }
+    for name, tensor in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), tensor.float().cpu().numpy())
+    log(f"wrote {', '.join(f'{name}.npy' for name in arrays)} to {dirname}")
 
 
 def main():
@@ -50,6 +92,12 @@ def main():
     parser.add_argument("--hipgraph", type=str, default="auto", choices=["auto", "on", "off"],
                         help="capture the fwd+bwd region in a hipGraph and replay it per step "
                              "(auto: try, fall back to eager on capture failure)")
+    parser.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                        help="after the timed steps, write the last step's loss, logits and the updated "
+                             "parameters as DIR/<name>.npy (float32; large arrays as a fixed seeded sample)")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the measurements that the headline figure does not need; the "
+                             "plain run already measures nothing else, so today this adds no work")
     args = parser.parse_args()
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -200,6 +248,8 @@ def main():
         return input_ids, labels
 
     graph_state = {}
+    # the logits outlive their step only when they are to be dumped (rank 0 writes)
+    keep_logits = args.dump_outputs is not None and rank == 0
 
     def try_capture_hipgraph():
         """Capture fwd+bwd once; per-step we copy fresh data into the static
@@ -221,9 +271,14 @@ def main():
         torch.cuda.synchronize(device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            static_loss, _ = model(static_ids, labels=static_labels)
+            static_loss, static_logits = model(static_ids, labels=static_labels)
             static_loss.backward()
         graph_state.update(graph=graph, ids=static_ids, labels=static_labels, loss=static_loss)
+        if keep_logits:
+            # holding the captured logits keeps their block out of the graph
+            # pool's reuse, so each replay leaves them intact for the dump
+            graph_state.update(logits=static_logits)
+        del static_logits
         log("hipGraph capture of fwd+bwd succeeded")
 
     def one_step():
@@ -235,13 +290,13 @@ def main():
             loss = graph_state["loss"]
             opt.step()
             opt.zero_grad(set_to_none=False)  # keep the graph's grad buffers
-            return loss
+            return loss, graph_state.get("logits")
         input_ids, labels = make_batch()
-        loss, _ = model(input_ids, labels=labels)
+        loss, logits = model(input_ids, labels=labels)
         loss.backward()
         opt.step()
         opt.zero_grad()
-        return loss
+        return loss, (logits if keep_logits else None)
 
     if use_gpu and args.hipgraph in ("auto", "on"):
         try:
@@ -287,10 +342,14 @@ def main():
     epoch_before = opt.local_epoch
     step_times = []
     epoch_steps = []  # wall time of steps in which an epoch transition landed
+    last_outputs = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         e0, s0 = opt.local_epoch, time.perf_counter()
-        one_step()
+        if keep_logits and i == args.steps - 1:
+            last_outputs = one_step()
+        else:
+            one_step()
         dt = time.perf_counter() - s0
         step_times.append(dt)
         if opt.local_epoch != e0:
@@ -312,6 +371,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=bench_pg)
         elapsed = float(t.item())
+
+    if last_outputs is not None:
+        if args.dpu:
+            # a delayed update may still be writing the parameters
+            opt.state_averager.step(wait_for_delayed_updates=True)
+        dump_outputs(args.dump_outputs, *last_outputs, model.parameters())
 
     total_samples = args.steps * args.batch * n_gpus
     samples_per_sec = total_samples / elapsed
