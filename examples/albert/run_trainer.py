@@ -43,9 +43,11 @@ def main():
     parser.add_argument("--batch_size", type=int, default=128)
     parser.add_argument("--seq_len", type=int, default=512)
     parser.add_argument("--lr", type=float, default=0.00176)
-    parser.add_argument("--optimizer", choices=["lamb", "adamw"], default="lamb",
+    parser.add_argument("--optimizer", choices=["lamb", "fused_lamb", "adamw"], default="lamb",
                         help="lamb = the reference recipe (LAMB + gradient clipping, "
-                             "examples/albert/run_trainer.py:266); adamw = FusedAdamW")
+                             "examples/albert/run_trainer.py:266); fused_lamb = the same "
+                             "mathematics as multi-tensor HIP kernels with no host sync "
+                             "(ops.FusedLamb); adamw = FusedAdamW")
     parser.add_argument("--clip_grad_norm", type=float, default=1.0)
     parser.add_argument("--max_epochs", type=int, default=10**9)
     parser.add_argument("--statistics_every", type=int, default=10)
@@ -88,6 +90,12 @@ def main():
 
         opt_factory = ClippingWrapper.create(
             Lamb, lr=args.lr, weight_decay=0.01, clip_grad_norm=args.clip_grad_norm
+        )
+    elif args.optimizer == "fused_lamb":
+        from hivemind_amd.ops import FusedLamb
+
+        opt_factory = lambda pg: FusedLamb(
+            pg, lr=args.lr, weight_decay=0.01, max_grad_norm=args.clip_grad_norm
         )
     else:
         opt_factory = lambda pg: FusedAdamW(pg, lr=args.lr, weight_decay=0.01)

@@ -504,6 +504,144 @@ class Lamb(torch.optim.Optimizer):
         return loss
 
 
+class FusedLamb(torch.optim.Optimizer):
+    """LAMB with optional global grad-norm clipping whose step never waits for
+    the device: the mathematics of ``ClippingWrapper(Lamb(...), max_grad_norm)``
+    (plain ``Lamb`` when ``max_grad_norm`` is None), except that gradients are
+    left unscaled -- the clip coefficient stays on the device and is applied as
+    the kernels load ``g``.
+
+    CUDA fp32 contiguous params with fp32/bf16 contiguous grads run the
+    multi-tensor HIP kernels (ops/hip/multi_tensor.hip): one launch sequence per
+    (group, step-count) bucket, per-tensor trust ratios reduced on the device.
+    Everything else (CPU tensors included) takes a torch path with the same
+    formulas and no host read either. State keys match ``Lamb``, so state dicts
+    interchange. ``last_trust_ratios`` maps param -> 0-dim tensor for logging.
+    """
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01,
+                 clamp_trust_ratio=(0.0, 10.0), max_grad_norm=None, mirrors=None):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__(params, defaults)
+        self.clamp_trust_ratio = clamp_trust_ratio
+        self.max_grad_norm = max_grad_norm
+        self._mirrors = mirrors or {}
+        self.last_trust_ratios = {}
+
+    def set_mirror(self, param: torch.Tensor, mirror: torch.Tensor):
+        self._mirrors[param] = mirror
+
+    @staticmethod
+    def _kernel_eligible(p: torch.Tensor, state) -> bool:
+        g = p.grad
+        return (
+            p.is_cuda
+            and p.dtype == torch.float32
+            and p.is_contiguous()
+            and g.device == p.device
+            and g.is_contiguous()
+            and g.dtype in (torch.float32, torch.bfloat16)
+            and all(
+                s.device == p.device and s.dtype == torch.float32 and s.is_contiguous()
+                for s in (state["exp_avg"], state["exp_avg_sq"])
+            )
+        )
+
+    def _clip_coefficients(self, kernel_grads, fallback_grads):
+        """device -> one-element fp32 tensor min(1, max_norm / (||g|| + 1e-6)),
+        the norm taken over every grad of this step (clip_grad_norm_'s formula)."""
+        sumsq = {}
+        for device, grads in kernel_grads.items():
+            sumsq[device] = torch.zeros(1, dtype=torch.float32, device=device)
+            hip_ops().multi_grad_sumsq_(grads, sumsq[device])
+        for device, g in fallback_grads:  # device: the param's, where its coefficient is needed
+            if device not in sumsq:
+                sumsq[device] = torch.zeros(1, dtype=torch.float32, device=device)
+            sumsq[device].add_(g.float().square().sum().to(device))
+        devices = list(sumsq)
+        total = sumsq[devices[0]]
+        for device in devices[1:]:  # params spread over devices: the copies order the streams
+            total = total + sumsq[device].to(devices[0])
+        clip = (self.max_grad_norm / (total.sqrt() + 1e-6)).clamp_(max=1.0)
+        return {device: clip if device == devices[0] else clip.to(device) for device in devices}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        lo, hi = self.clamp_trust_ratio
+        buckets = {}  # (group index, step) -> ([p], [g], [m], [v], [kernel mirror], [(p, mirror, kernel mirror)])
+        fallback = []  # (group, p, state)
+        kernel_grads = {}  # device -> [g]
+        for group_index, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = 0
+                    state["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
+                    state["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
+                state["step"] += 1
+                if self._kernel_eligible(p, state):
+                    mirror = self._mirrors.get(p)
+                    kernel_mirror = mirror if (
+                        mirror is not None and mirror.dtype == torch.bfloat16 and mirror.is_contiguous()
+                        and mirror.device == p.device and mirror.numel() == p.numel()
+                    ) else None
+                    bucket = buckets.setdefault((group_index, state["step"]), ([], [], [], [], [], []))
+                    bucket[0].append(p.data)
+                    bucket[1].append(p.grad)
+                    bucket[2].append(state["exp_avg"])
+                    bucket[3].append(state["exp_avg_sq"])
+                    bucket[4].append(kernel_mirror)
+                    bucket[5].append((p, mirror, kernel_mirror))
+                    kernel_grads.setdefault(p.device, []).append(p.grad)
+                else:
+                    fallback.append((group, p, state))
+
+        clip = {}
+        if self.max_grad_norm is not None and (buckets or fallback):
+            clip = self._clip_coefficients(kernel_grads, [(p.device, p.grad) for _, p, _ in fallback])
+
+        for (group_index, step_count), bucket in buckets.items():
+            group = self.param_groups[group_index]
+            beta1, beta2 = group["betas"]
+            trust = hip_ops().multi_lamb_(
+                bucket[0], bucket[1], bucket[2], bucket[3], bucket[4],
+                group["lr"], beta1, beta2, group["eps"], group["weight_decay"], step_count,
+                lo, hi, clip.get(bucket[0][0].device),
+            )
+            for (p, mirror, kernel_mirror), ratio in zip(bucket[5], trust.unbind(0)):
+                self.last_trust_ratios[p] = ratio
+                if mirror is not None and kernel_mirror is None:
+                    mirror.copy_(p.data.to(mirror.dtype))
+
+        for group, p, state in fallback:
+            beta1, beta2 = group["betas"]
+            g = p.grad.float().to(p.device)
+            if p.device in clip:
+                g = g * clip[p.device]  # a new tensor: p.grad itself stays as it is
+            m, v = state["exp_avg"], state["exp_avg_sq"]
+            m.mul_(beta1).add_(g, alpha=1 - beta1)
+            v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            m_hat = m / (1 - beta1 ** state["step"])
+            v_hat = v / (1 - beta2 ** state["step"])
+            update = m_hat / (v_hat.sqrt() + group["eps"])
+            if group["weight_decay"]:
+                update = update + group["weight_decay"] * p.float()
+            p_norm = p.detach().float().norm()
+            u_norm = update.norm()
+            trust_ratio = torch.where(
+                (p_norm > 0) & (u_norm > 0), p_norm / u_norm, torch.ones_like(p_norm)
+            ).clamp(lo, hi)
+            p.data.sub_((update * (trust_ratio * group["lr"])).to(p.dtype))
+            self.last_trust_ratios[p] = trust_ratio
+            mirror = self._mirrors.get(p)
+            if mirror is not None:
+                mirror.copy_(p.data.to(mirror.dtype))
+        return loss
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW whose step is one HIP kernel per parameter on the GPU.
 

@@ -541,6 +541,165 @@ void multi_accumulate_(std::vector<torch::Tensor> accs, std::vector<torch::Tenso
   }
 }
 
+// ---- LAMB: chunk table + alignment bookkeeping shared by the two bindings
+
+namespace {
+
+// elements to peel until `ptr` (elements of elem_size bytes) sits on a
+// 4-element boundary; -1 if no element count gets it there
+inline int mt_vec_head(const void* ptr, int elem_size) {
+  uintptr_t a = reinterpret_cast<uintptr_t>(ptr);
+  uintptr_t span = 4 * (uintptr_t)elem_size;
+  if (a % elem_size != 0) return -1;
+  return (int)(((span - a % span) % span) / elem_size);
+}
+
+inline bool mt_vec_aligned(const void* ptr, int head, int elem_size) {
+  uintptr_t a = reinterpret_cast<uintptr_t>(ptr) + (uintptr_t)head * elem_size;
+  return a % (4 * (uintptr_t)elem_size) == 0;
+}
+
+inline long long mt_lamb_blocks(long long numel, int head) {
+  if (numel <= 0) return 0;
+  long long body = head < 0 ? numel : numel - head;
+  long long blocks = (body + MT_LAMB_CHUNK - 1) / MT_LAMB_CHUNK;
+  return blocks < 1 ? 1 : blocks;  // a tensor that is all head still needs its block
+}
+
+inline void check_lamb_grad(const torch::Tensor& g, const torch::Tensor& like, size_t t) {
+  TORCH_CHECK(g.is_cuda() && g.device() == like.device(), "grad ", t, " must be on the params' GPU");
+  TORCH_CHECK(g.is_contiguous(), "grad ", t, " must be contiguous");
+  TORCH_CHECK(g.scalar_type() == torch::kFloat32 || g.scalar_type() == torch::kBFloat16,
+              "grads must be fp32 or bf16");
+}
+
+}  // namespace
+
+void multi_grad_sumsq_(std::vector<torch::Tensor> grads, torch::Tensor out) {
+  CHECK_GPU(out);
+  TORCH_CHECK(out.scalar_type() == torch::kFloat32 && out.numel() == 1 && out.is_contiguous(),
+              "multi_grad_sumsq_: out must be a one-element fp32 tensor");
+  size_t n = grads.size();
+  std::vector<int> heads(n);
+  long long total_blocks = 0;
+  for (size_t t = 0; t < n; ++t) {
+    check_lamb_grad(grads[t], out, t);
+    int elem = grads[t].scalar_type() == torch::kBFloat16 ? 2 : 4;
+    int head = mt_vec_head(grads[t].data_ptr(), elem);
+    if (head > grads[t].numel()) head = (int)grads[t].numel();
+    heads[t] = head;
+    total_blocks += mt_lamb_blocks(grads[t].numel(), head);
+  }
+  if (total_blocks == 0) return;
+  TORCH_CHECK(total_blocks < (1ll << 31), "multi_grad_sumsq_: too many elements");
+  auto partials = torch::empty({total_blocks}, out.options());
+  long long done = 0;
+  for (size_t start = 0; start < n; start += MT_CHUNK) {
+    MTSumsqArgs args{};
+    args.n = 0;
+    args.cumblk[0] = 0;
+    args.g_bf16_mask = 0;
+    for (size_t t = start; t < n && args.n < MT_CHUNK; ++t, ++args.n) {
+      int i = args.n;
+      args.g[i] = grads[t].data_ptr();
+      if (grads[t].scalar_type() == torch::kBFloat16) args.g_bf16_mask |= (1ull << i);
+      args.numel[i] = grads[t].numel();
+      args.head[i] = heads[t];
+      args.cumblk[i + 1] = args.cumblk[i] + (int)mt_lamb_blocks(grads[t].numel(), heads[t]);
+    }
+    launch_multi_tensor_grad_sumsq(&args, partials.data_ptr<float>() + done,
+                                   (void*)current_stream());
+    done += args.cumblk[args.n];
+  }
+  launch_sumsq_finalize(partials.data_ptr<float>(), total_blocks, out.data_ptr<float>(),
+                        (void*)current_stream());
+}
+
+torch::Tensor multi_lamb_(std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads,
+                          std::vector<torch::Tensor> exp_avgs, std::vector<torch::Tensor> exp_avg_sqs,
+                          std::vector<c10::optional<torch::Tensor>> mirrors,
+                          double lr, double beta1, double beta2, double eps, double weight_decay,
+                          int64_t step, double trust_lo, double trust_hi,
+                          c10::optional<torch::Tensor> clip_coef) {
+  size_t n = params.size();
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n &&
+              mirrors.size() == n, "multi_lamb_: list length mismatch");
+  TORCH_CHECK(n > 0, "multi_lamb_: empty parameter list");
+  TORCH_CHECK(step >= 1, "multi_lamb_: step counts from 1");
+  auto fp32_opts = params[0].options().dtype(torch::kFloat32);
+  const float* clip_ptr = nullptr;
+  if (clip_coef.has_value()) {
+    auto& c = clip_coef.value();
+    TORCH_CHECK(c.is_cuda() && c.device() == params[0].device() && c.numel() == 1 &&
+                c.scalar_type() == torch::kFloat32 && c.is_contiguous(),
+                "multi_lamb_: clip_coef must be a one-element fp32 tensor on the params' GPU");
+    clip_ptr = c.data_ptr<float>();
+  }
+  std::vector<int> heads(n);
+  long long total_blocks = 0;
+  for (size_t t = 0; t < n; ++t) {
+    auto& p = params[t];
+    CHECK_GPU(p); CHECK_CONTIG(p);
+    TORCH_CHECK(p.device() == params[0].device(), "multi_lamb_: params must share one GPU");
+    TORCH_CHECK(p.scalar_type() == torch::kFloat32, "multi_lamb_ params must be fp32 masters");
+    check_lamb_grad(grads[t], p, t);
+    TORCH_CHECK(grads[t].numel() == p.numel(), "bad grad ", t);
+    for (const torch::Tensor* s : {&exp_avgs[t], &exp_avg_sqs[t]}) {
+      TORCH_CHECK(s->is_cuda() && s->device() == p.device() && s->is_contiguous() &&
+                  s->scalar_type() == torch::kFloat32 && s->numel() == p.numel(),
+                  "multi_lamb_: exp_avg/exp_avg_sq ", t, " must be contiguous fp32 on the params' GPU");
+    }
+    if (mirrors[t].has_value()) {
+      auto& mir = mirrors[t].value();
+      TORCH_CHECK(mir.is_cuda() && mir.device() == p.device() && mir.is_contiguous() &&
+                  mir.scalar_type() == torch::kBFloat16 && mir.numel() == p.numel(),
+                  "multi_lamb_: mirror ", t, " must be contiguous bf16 on the params' GPU");
+    }
+    bool g_bf16 = grads[t].scalar_type() == torch::kBFloat16;
+    int head = mt_vec_head(p.data_ptr(), 4);
+    if (head >= 0 &&
+        !(mt_vec_aligned(exp_avgs[t].data_ptr(), head, 4) &&
+          mt_vec_aligned(exp_avg_sqs[t].data_ptr(), head, 4) &&
+          mt_vec_aligned(grads[t].data_ptr(), head, g_bf16 ? 2 : 4) &&
+          (!mirrors[t].has_value() || mt_vec_aligned(mirrors[t]->data_ptr(), head, 2))))
+      head = -1;
+    if (head > p.numel()) head = (int)p.numel();
+    heads[t] = head;
+    total_blocks += mt_lamb_blocks(p.numel(), head);
+  }
+  TORCH_CHECK(total_blocks < (1ll << 31), "multi_lamb_: too many elements");
+  auto trust = torch::empty({(long long)n}, fp32_opts);
+  // {sum p^2, sum u^2} per block
+  auto partials = torch::empty({total_blocks > 0 ? total_blocks : 1, 2}, fp32_opts);
+  double bias_corr1 = 1.0 - std::pow(beta1, (double)step);
+  double bias_corr2 = 1.0 - std::pow(beta2, (double)step);
+  long long done = 0;
+  for (size_t start = 0; start < n; start += MT_CHUNK) {
+    MTLambArgs args{};
+    args.n = 0;
+    args.cumblk[0] = 0;
+    args.g_bf16_mask = 0;
+    for (size_t t = start; t < n && args.n < MT_CHUNK; ++t, ++args.n) {
+      int i = args.n;
+      args.p[i] = params[t].data_ptr<float>();
+      args.g[i] = grads[t].data_ptr();
+      if (grads[t].scalar_type() == torch::kBFloat16) args.g_bf16_mask |= (1ull << i);
+      args.m[i] = exp_avgs[t].data_ptr<float>();
+      args.v[i] = exp_avg_sqs[t].data_ptr<float>();
+      args.mirror[i] = mirrors[t].has_value() ? (mt_ushort*)mirrors[t]->data_ptr() : nullptr;
+      args.numel[i] = params[t].numel();
+      args.head[i] = heads[t];
+      args.cumblk[i + 1] = args.cumblk[i] + (int)mt_lamb_blocks(params[t].numel(), heads[t]);
+    }
+    launch_multi_tensor_lamb(&args, (float)lr, beta1, beta2, (float)eps,
+                             (float)weight_decay, bias_corr1, bias_corr2, (float)trust_lo,
+                             (float)trust_hi, clip_ptr, partials.data_ptr<float>() + 2 * done,
+                             trust.data_ptr<float>() + start, (void*)current_stream());
+    done += args.cumblk[args.n];
+  }
+  return trust;
+}
+
 // ------------------------------------------------------------- attention
 
 static void check_flash_shapes(const torch::Tensor& t, const char* name) {
@@ -665,4 +824,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_bhsd", &transpose_bhsd, "[B,H,S,D] -> [B,H,D,S] in-register 8x8 transpose");
   m.def("multi_adamw_", &multi_adamw_, "one-launch AdamW step over a parameter list");
   m.def("multi_accumulate_", &multi_accumulate_, "one-launch acc += alpha*x over a tensor list");
+  m.def("multi_lamb_", &multi_lamb_,
+        "multi-tensor LAMB step with on-device trust ratios -> trust ratios [n]");
+  m.def("multi_grad_sumsq_", &multi_grad_sumsq_, "out[0] += sum of squares over a grad list");
 }
